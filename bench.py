@@ -6,9 +6,12 @@ payloads, one CRC32 each, bit-exact with the reference's client/checksum.cc. One
 one launch of the batched kernel over one 256 MiB batch already resident in HBM. Four
 distinct batches are rotated so the 256 MiB Infinity Cache cannot serve re-reads (every
 step reads HBM). Payloads are synthetic (SURVEY.md 8d generator), generated on device
-before timing. The same run also times configs C (1 Mi ragged messages), D (256 x 64 MiB,
-ragged and uniform API) and S (config B in the reference's slot layout: publish and
-verify), each checked bit-exact, under "configs".
+before timing. A plain run does only that: set up, settle, warm up, time the K steps,
+print the line. With --full the same run also checks the headline's CRCs against the
+fixture, measures the read ceiling, times configs C (1 Mi ragged messages), D (256 x 64
+MiB, ragged and uniform API) and S (config B in the reference's slot layout: publish and
+verify), each checked bit-exact, under "configs", the PCIe end-to-end leg and the CPU
+baseline; without it those fields of the line are null.
 
 Workload at N > 1 (BASELINE.json configs[4], "config E"): 8 Mi x 4 KiB payloads sharded
 round-robin over the GPUs (strong scaling), one RCCL all_gather of the 4-byte CRCs after
@@ -16,7 +19,9 @@ the timed region (timed separately), the whole list checked against the fixture;
 then times the same 8 Mi batch alone on its GPU, and the line reports per-GPU value and
 efficiency = value / (N x that single-GPU rate).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload B|C|E]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload B|C|E] [--full] [--dump-outputs DIR]
+      --dump-outputs DIR: the CRCs the last timed step stored, as DIR/crc32.npy (float64);
+      the payloads come from fixed seeds, so the same arguments give the same file.
       With N > 1 and no WORLD_SIZE in the environment, this process only spawns N ranks
       (python -m torch.distributed.run, one process per GPU, RCCL) and exits with their
       status; it never touches a GPU itself.
@@ -30,7 +35,7 @@ efficiency = value / (N x that single-GPU rate).
 
 Prints ONE JSON line (rank 0). `value` = aggregate GiB/s over all ranks (bytes of all ranks
 / max-over-ranks time between barriers). `roofline` is for the dominant kernel (one HIP
-event pair around the K launches on their stream, / K). `cpu_baseline` times the oracle
+event pair around the K launches on their stream, / K). `cpu_baseline` (--full) times the oracle
 (a C restatement of the reference table path) on this host's cores over bounded samples
 of configs B, C, D and E (median of 5 runs each, 1 core and all cores available to the
 job).
@@ -112,6 +117,15 @@ def parse():
                     help="each rank prints the launch environment it got (one JSON line) and exits, for tests")
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="CPU + gloo rehearsal of the spawn/shard/gather path (host SubspaceCRC32), for tests")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline also run everything else the line can carry -- the fixture "
+                         "check of the headline's CRCs, the read-ceiling probe, the secondary configs (--configs), "
+                         "the PCIe end-to-end leg and the CPU baseline (minutes). Off by default: a plain run sets "
+                         "up, settles, warms up, times the K steps and prints the line, those fields null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the CRCs the last timed step stored (what a caller of that "
+                         "step receives) to DIR/crc32.npy (float64, one value per message; DIR/crc32_rank<r>.npy "
+                         "per rank at N > 1)")
     return ap.parse_args()
 
 
@@ -156,6 +170,26 @@ def spawn_ranks(args) -> int:
 
 def digest(crcs) -> str:
     return hashlib.sha256(np.asarray(crcs, dtype="<u4").tobytes()).hexdigest()
+
+
+DUMP_MAX = 2 << 20  # values per dumped array (16 MiB as float64, as much again for a sample's indices)
+
+
+def dump_outputs(dirname, rank, world, crcs) -> None:
+    """--dump-outputs: this rank's CRCs of the last timed step as DIR/crc32.npy (float64: every
+    32-bit CRC is exact in it), DIR/crc32_rank<r>.npy at N > 1. The inputs are generated from
+    fixed seeds, so two builds run with the same arguments can be compared value for value. A
+    list longer than DUMP_MAX is sampled at fixed (seeded, sorted) message indices, written
+    beside it as <name>_index.npy."""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    name = "crc32" if world == 1 else f"crc32_rank{rank}"
+    a = np.asarray(crcs).view(np.uint32)
+    if a.size > DUMP_MAX:
+        idx = np.sort(np.random.default_rng(0x5EED0D09).choice(a.size, DUMP_MAX, replace=False))
+        np.save(d / f"{name}_index.npy", idx.astype(np.float64))
+        a = a[idx]
+    np.save(d / f"{name}.npy", a.astype(np.float64))
 
 
 # ------------------------------------------------------------------------------ CPU baseline
@@ -430,6 +464,11 @@ class Workload:
             return
         self.ctx.crc32_uniform(self.bufs[k], MSG_BYTES, MSG_BYTES, self.nmsg, self.outs[k],
                                stream=streams[i % len(streams)])
+
+    def last_output(self, steps):
+        """The CRCs (host int32 array, one per message of this rank) that step `steps` - 1, the
+        last of a timed region of `steps` steps, stored."""
+        return self.outs[(steps - 1) % self.nbuf][:self.nmsg].cpu().numpy()
 
     def check(self, dist):
         """(bit-exact vs the fixture on rank 0, gather timing). Collective when world > 1: the
@@ -1167,6 +1206,8 @@ def dry_run_cpu(args, world, rank) -> int:
     else:
         full = local[:len(msgs)]
     gather_ms = (time.perf_counter() - tg) * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, local[:len(msgs)])
     me = {"rank": rank, "local_rank": int(os.environ.get("LOCAL_RANK", "0")), "device": "cpu", "pid": os.getpid(),
           "step_ms": round(own / args.steps * 1e3, 4)}
     everyone = [me]
@@ -1261,10 +1302,14 @@ def main():
                                                                 RoctxRegion(args.roctx_region and rank == 0),
                                                                 args.settle_s if args.settle > 0 else 0.0)
     settle = max(0, settle - args.warmup)
-    bitexact, gather = wl.check(pg)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, wl.last_output(args.steps))
+    # everything below the headline's own timing is --full's at N = 1; an N-rank line keeps its
+    # gather, check and single-GPU leg (its efficiency is part of that line's headline)
+    bitexact, gather = wl.check(pg) if args.full or world > 1 else (None, None)
     gather_ms = gather["gather_ms"] if gather else None
     ceiling = None
-    if args.workload == "B" and world == 1:
+    if args.full and args.workload == "B" and world == 1:
         try:
             ceiling = read_ceiling(wl)
         except Exception as e:  # an extra leg must never cost the headline line
@@ -1323,14 +1368,14 @@ def main():
     configs = None
     cfg_names = args.configs if args.configs is not None else ("C,Cu,D,Du,S,Usmall,S_short,S_mixed,S_large" if args.workload == "B"
                                                                else "none")
-    if world == 1 and cfg_names != "none":
+    if args.full and world == 1 and cfg_names != "none":
         configs = optional(lambda: secondary_configs(ctx, dev, [c for c in cfg_names.split(",") if c],
                                                      args.config_iters))
     e2e = None
-    if world == 1 and not args.no_e2e and args.workload == "B":
+    if args.full and world == 1 and not args.no_e2e and args.workload == "B":
         e2e = optional(lambda: end_to_end(ctx, gpu))
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and args.workload == "B":
+    if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "B":
         def cpu_leg():
             wl_b = Workload("B", ctx, dev, 1, 0)
             samples = cpu_samples(dev, wl_b.bufs)
@@ -1394,6 +1439,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "settle_launches": settle,
+            "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": scaling,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the committed golden fixtures in tests/golden/.
 
-  python tests/golden/make_golden.py            # small vectors  -> golden.json
+  python tests/golden/make_golden.py            # small vectors  -> golden.json, crc32_table.json
   python tests/golden/make_golden.py --configs  # + full-size synthetic config hashes -> configs.json
   python tests/golden/make_golden.py --small    # only the small config prefixes (B_small, C_small,
                                                 # C_2k), merged into the existing configs.json
@@ -144,6 +144,16 @@ def small_vectors(oracle) -> dict:
     return out
 
 
+def byte_table(oracle) -> dict:
+    """The 256 entries of the reflected IEEE byte table, each from zlib: entry b is the raw
+    state after the one byte b from state 0 (the table the reference's default build indexes,
+    client/checksum.cc:79-122)."""
+    table = [ref_raw(0, bytes([b])) for b in range(256)]
+    assert table == oracle.table()
+    return {"generator": "tests/golden/make_golden.py", "zlib_version": zlib.ZLIB_VERSION,
+            "what": "table[b] = ~zlib.crc32(bytes([b]), 0xFFFFFFFF) & 0xFFFFFFFF", "table": table}
+
+
 def list_hash(crcs: np.ndarray) -> str:
     return hashlib.sha256(np.ascontiguousarray(crcs, dtype="<u4").tobytes()).hexdigest()
 
@@ -189,6 +199,8 @@ def main():
     vec = small_vectors(oracle)
     (HERE / "golden.json").write_text(json.dumps(vec, indent=1) + "\n")
     print("wrote golden.json")
+    (HERE / "crc32_table.json").write_text(json.dumps(byte_table(oracle)) + "\n")
+    print("wrote crc32_table.json")
     if args.configs:
         cfg = config_hashes(oracle, args.threads)
         (HERE / "configs.json").write_text(json.dumps(cfg, indent=1) + "\n")

@@ -62,6 +62,20 @@ def test_dry_run_single_rank_default_workload():
     assert line["n_gpus"] == 1 and line["bitexact_vs_golden"] is True and line["scaling"] == "weak"
 
 
+def test_dump_outputs_writes_the_last_steps_crcs(tmp_path):
+    """--dump-outputs DIR leaves DIR/crc32.npy: float64, one CRC per message of the last timed
+    step, here the 4,096-message B_small fixture batch."""
+    import hashlib
+
+    import numpy as np
+    gold = json.loads((ROOT / "tests" / "golden" / "configs.json").read_text())["B_small"]
+    r = run_bench("--dry-run-cpu", "--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "out"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    a = np.load(tmp_path / "out" / "crc32.npy")
+    assert a.dtype == np.float64 and a.shape == (gold["count"],)
+    assert hashlib.sha256(a.astype("<u4").tobytes()).hexdigest() == gold["sha256_le_u32"]
+
+
 def test_world_size_must_match_gpus():
     r = run_bench("--gpus", "2", "--dry-run-cpu", env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode == 2
@@ -156,8 +170,8 @@ def test_both_launch_forms_give_ranks_the_same_environment():
 
 
 def test_default_secondary_configs_cover_every_row():
-    """the driver's default line carries Cu (config C at unaligned
-    offsets) and S_large (the reference's 32 KiB checksum channel) beside the other rows."""
+    """the default config list (run under --full) carries Cu (config C
+    at unaligned offsets) and S_large (the reference's 32 KiB checksum channel) beside the other rows."""
     import re
     src = (Path(__file__).resolve().parent.parent / "bench.py").read_text()
     m = re.search(r'cfg_names = args\.configs if args\.configs is not None else \("([^"]+)"', src)

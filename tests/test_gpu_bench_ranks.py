@@ -58,7 +58,7 @@ def test_rccl_path_one_rank():
         port = s.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"),
-                        "--gpus", "1", "--workload", "E", "--steps", "3", "--warmup", "1", "--settle", "0"],
+                        "--gpus", "1", "--workload", "E", "--steps", "3", "--warmup", "1", "--settle", "0", "--full"],
                        capture_output=True, text=True, timeout=400, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -69,13 +69,37 @@ def test_rccl_path_one_rank():
     assert d["config"]["gather"]["gather_ms"] > 0 and d["ranks"][0]["rank"] == 0
 
 
+def test_plain_run_times_only_the_headline_and_dumps_its_crcs(tmp_path):
+    """Without --full the N = 1 run carries no extra leg (no fixture check, read ceiling,
+    secondary config, end-to-end or CPU-baseline figure), and --dump-outputs leaves the last
+    timed step's CRCs: with 5 steps over 4 rotated batches that is batch 0, config B itself."""
+    import hashlib
+
+    import numpy as np
+    gold = json.loads((ROOT / "tests" / "golden" / "configs.json").read_text())["B"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1",
+                        "--settle", "0", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=400, env=env, cwd=str(ROOT))
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 5 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["configs"] is None and d["cpu_baseline"] is None and d["e2e_pcie"] is None
+    assert d["bitexact_vs_golden"] is None and "read_ceiling" not in d["roofline"]
+    a = np.load(tmp_path / "crc32.npy")
+    assert a.dtype == np.float64 and a.shape == (gold["count"],)
+    assert hashlib.sha256(a.astype("<u4").tobytes()).hexdigest() == gold["sha256_le_u32"]
+
+
 def test_single_gpu_line_reports_read_ceiling():
     """The N = 1 config-B line carries the measured read ceiling of the same access shape
     (SURVEY.md 8d): the stream-read probe over the same rotated batches, and the CRC kernel's
     fraction of it (< 1: the CRC kernel reads the same bytes plus its compute)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "50", "--warmup", "2", "--settle", "0",
-                        "--configs", "none", "--no-cpu-baseline", "--no-e2e"],
+                        "--full", "--configs", "none", "--no-cpu-baseline", "--no-e2e"],
                        capture_output=True, text=True, timeout=400, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -1,20 +1,18 @@
 """Pin the oracle (oracle/crc32_oracle.c) before trusting it as the checker.
 
 Pins: the golden fixtures (zlib-derived, tests/golden/make_golden.py), the
-reference's own literal tests (rust_client/tests/client_test.rs:169-218), and --
-when the reference checkout is present in this container -- the 256 table
-constants of the reference's default-build path (client/checksum.cc:79-122).
+reference's own literal tests (rust_client/tests/client_test.rs:169-218), and the
+256 constants of the byte table that the reference's default-build path indexes
+(client/checksum.cc:79-122), as the zlib-derived fixture tests/golden/crc32_table.json.
 """
 import json
-import re
 import zlib
 from pathlib import Path
 
 import numpy as np
-import pytest
 
 GOLDEN = json.loads((Path(__file__).parent / "golden" / "golden.json").read_text())
-REFERENCE_CHECKSUM_CC = Path("/root/reference/client/checksum.cc")
+BYTE_TABLE = json.loads((Path(__file__).parent / "golden" / "crc32_table.json").read_text())["table"]
 M32 = 0xFFFFFFFF
 
 
@@ -23,15 +21,12 @@ def test_table_is_reflected_ieee(oracle):
     assert t[1] == 0x77073096 and t[128] == 0xEDB88320 and t[255] == 0x2D02EF8D
 
 
-@pytest.mark.skipif(not REFERENCE_CHECKSUM_CC.exists(), reason="reference checkout not present")
 def test_table_matches_reference_source(oracle):
-    """Compare with the constants in client/checksum.cc:79-122 (read as text, not copied)."""
-    src = REFERENCE_CHECKSUM_CC.read_text()
-    body = src[src.index("crc32_table[256]"):]
-    body = body[:body.index("};")]
-    ref = [int(x, 16) for x in re.findall(r"0x([0-9A-Fa-f]{8})", body)]
-    assert len(ref) == 256
-    assert ref == oracle.table()
+    """All 256 constants of the table in client/checksum.cc:79-122, held as the committed
+    fixture: each entry derived from zlib (entry b = the raw state after byte b from state 0,
+    tests/golden/make_golden.py), so the test needs no reference checkout."""
+    assert len(BYTE_TABLE) == 256
+    assert BYTE_TABLE == oracle.table()
 
 
 def test_kats(oracle):

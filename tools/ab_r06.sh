@@ -67,7 +67,7 @@ case ",$STEPS," in *,tl,*)
   done ;;
 esac
 case ",$STEPS," in *,bench,*)
-  timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
   stop $? bench ;;
 esac
 echo done >> "$OUT/status.txt"

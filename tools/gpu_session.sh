@@ -11,6 +11,7 @@ STEPS=${*:-"test smoke bench profsel pmc"}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
+ROOT=$(cd "$(dirname "$0")/.." && pwd)  # the repository (the profiler steps run from /tmp)
 
 stop_if_fault() {  # $1 = exit status, $2 = step name
   local rc=$1
@@ -34,12 +35,12 @@ for s in $STEPS; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
       stop_if_fault $? smoke ;;
     bench)
-      timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+      timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
       stop_if_fault $? bench ;;
     prof)
-      (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$OUT/prof" -o run \
-        --output-format csv -- python3 "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline \
-        --no-e2e > "$GRAFT_REPO_ROOT/$OUT/prof_bench.json" 2> "$GRAFT_REPO_ROOT/$OUT/prof.err")
+      (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/prof" -o run \
+        --output-format csv -- python3 "$ROOT/bench.py" --full --no-cpu-baseline \
+        --no-e2e > "$ROOT/$OUT/prof_bench.json" 2> "$ROOT/$OUT/prof.err")
       stop_if_fault $? prof ;;
     profsel)  # the timed region only: roctxProfilerResume/Pause around it (--marker-trace routes them to the tool)
       (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --marker-trace --selected-regions -d "$GRAFT_REPO_ROOT/$OUT/profsel" -o run \
@@ -48,9 +49,9 @@ for s in $STEPS; do
       stop_if_fault $? profsel ;;
     pmc)
       for ctr in FETCH_SIZE WRITE_SIZE; do
-        (cd /tmp && timeout -k 10 600 rocprofv3 --pmc $ctr -d "$GRAFT_REPO_ROOT/$OUT/pmc_$ctr" -o run \
-          --output-format csv -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 20 --warmup 2 --settle 0 --no-cpu-baseline \
-          --no-e2e > "$GRAFT_REPO_ROOT/$OUT/pmc_$ctr.json" 2> "$GRAFT_REPO_ROOT/$OUT/pmc_$ctr.err")
+        (cd /tmp && timeout -k 10 600 rocprofv3 --pmc $ctr -d "$ROOT/$OUT/pmc_$ctr" -o run \
+          --output-format csv -- python3 "$ROOT/bench.py" --full --steps 20 --warmup 2 --settle 0 --no-cpu-baseline \
+          --no-e2e > "$ROOT/$OUT/pmc_$ctr.json" 2> "$ROOT/$OUT/pmc_$ctr.err")
         stop_if_fault $? "pmc_$ctr"
       done ;;
     configs)
