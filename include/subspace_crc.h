@@ -91,13 +91,22 @@ int subspace_crc_ctx_check(subspace_crc_ctx* ctx, void* stream);
 int subspace_crc_ctx_reserve(subspace_crc_ctx* ctx, uint64_t max_messages, uint64_t max_tiles);
 
 /* Fixed-size batch: message i is the `length` bytes at dev_base + i*stride.
- * stride >= length. Any length (0 allowed); any stride. The kernels read only inside
- * [dev_base, dev_base + (count-1)*stride + length), the end rounded up to 16 bytes (gaps
- * between messages included: they are read and ignored). */
+ * stride >= length. Any length (0 allowed); any stride; dev_base may have any alignment
+ * (SubspaceCRC32's contract). A base on a 16-byte boundary with a stride that is a multiple of
+ * 16 takes the fast kernels (4 KiB messages, whole 8 KiB pieces, the small-message kernel's
+ * 16-byte-stride form); any other base gives the same results through the general forms.
+ * The kernels read whole 16-byte blocks counted from dev_base -- block b is
+ * [dev_base + 16 b, dev_base + 16 b + 16), whatever dev_base's own alignment -- and only inside
+ * [dev_base, dev_base + (count-1)*stride + length), the end rounded up to 16 bytes from
+ * dev_base (gaps between messages included: they are read and ignored). */
 int subspace_crc32_batch_uniform(subspace_crc_ctx* ctx, const void* dev_base, uint64_t stride, uint64_t length,
                                  uint64_t count, uint32_t init, uint32_t flags, uint32_t* dev_out, void* stream);
 
 /* Ragged batch: message i is the dev_lengths[i] bytes at dev_base + dev_offsets[i].
+ * dev_base may have any alignment, like every offset. A message is read as the whole 16-byte
+ * blocks, counted from dev_base as above, that hold one of its bytes: from
+ * dev_base + (offset & ~15) up to dev_base + offset + length rounded up to 16 (at most 15 bytes
+ * before its first and after its last byte, never before dev_base); an empty message reads nothing.
  * arena_bytes = bytes readable from dev_base (every message must lie inside it). It sizes the
  * tile workspace and, up to 2^37 bytes, selects the one-kernel tile-count scan + 8-byte tile
  * descriptors; a message found outside it still gets its correct CRC (the kernel then locates

@@ -604,10 +604,11 @@ def test_large_slot_list_latency_channel_shape(gpu_ctx, oracle, mode):
 
 @pytest.mark.parametrize("mode", ["publish", "verify"])
 def test_large_slot_list_statuses(gpu_ctx, oracle, mode):
-    """Slot lists past 4 KiB (the ragged path at absolute addresses, finished by its last
-    kernel: crc_slots.hip crc32_ragged_final_slot_kernel) with a metadata span, empty payloads
-    and records longer than max_message_size (a list's records carry their sizes: computed
-    whole, as on the small-kernel path), and for verify every status the oracle gives:
+    """Slot lists past 4 KiB (the ragged path at absolute addresses: its last kernel,
+    crc32_ragged_final_kernel, then crc_slots.hip crc32_slot_finish_kernel with its shift
+    operators staged in LDS) with a metadata span, empty payloads and records longer than
+    max_message_size (a list's records carry their sizes: computed whole, as on the
+    small-kernel path), and for verify every status the oracle gives:
     mismatches in the payload, metadata, span 0 and stored checksum, uncovered bytes changed,
     and slots without kMessageHasChecksum."""
     count, area, max_len, cs, ms = 1200, 32768, 20000, 4, 16
